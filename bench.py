@@ -3,17 +3,24 @@
 (BASELINE.json configs[1]: config_infonce.yaml recipe, v2-mini-shaped encoder, synthetic
 MS-MARCO triples, bs=32 x (1 pos + 15 negs), seq 128, bf16, dropout on, fused AdamW included).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
 One "step" = one optimisation step over one batch per rank; batches are resident in HBM
 before the timed region.  `value` is measured on the DENSE layout (every padded token row
-computed; the ragged rate the product's trainer runs at is reported beside it).  Rank 0 prints
-ONE JSON line (contract in the task statement) with two extra objects: "roofline" (the step's
-dominant kernel class, the encoder GEMMs, timed live with HIP events on the streams they run
-on; the fused head forward under "roofline_head_fwd") and "cpu_baseline" (the CPU oracle timed
-at the full configs[1] shape, 2 steps; N=1 only).
+computed).  Rank 0 prints ONE JSON line (contract in the task statement).
+
+A plain run sets up, warms up, times K steps and prints the line (`value`, `ms_per_step` and the
+liveness of the timed region).  --full adds everything else, after the timed region: the other
+layout (the ragged rate the product's trainer runs at), "roofline" (the step's dominant kernel
+class, the encoder GEMMs, timed live with HIP events on the streams they run on; the fused head
+forward under "roofline_head_fwd"), the measured peaks, the sparse-regime / configs[4] /
+sequence-sweep legs, "cpu_baseline" (the CPU oracle timed at the full configs[1] shape, 2 steps;
+N=1 only) and, at N > 1, the score-block exchange beside the all-gather one.
+
+--dump-outputs DIR writes what the last timed step handed its caller (losses, a fixed sample of
+the sparse document representations and of the updated parameters, the IDF vector) as DIR/*.npy.
 """
 import argparse
 import json
@@ -52,8 +59,8 @@ def parse():
     ap.add_argument("--layout", default="dense", choices=["ragged", "dense"],
                     help="layout `value` is measured on: dense = every document computed at the full padded length (SURVEY 8d "
                          "headline protocol, the default), ragged = padding tokens skipped on the device (what the product's "
-                         "trainer does by default: identical outputs); the other layout is timed too (after the timed region) "
-                         "and reported beside it")
+                         "trainer does by default: identical outputs); --full times the other layout too (after the timed region) "
+                         "and reports it beside it")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--bs", type=int, default=32)
     ap.add_argument("--negs", type=int, default=15)
@@ -75,6 +82,13 @@ def parse():
     ap.add_argument("--single-rank-rccl", action="store_true",
                     help="N = 1 only: initialise a ONE-rank process group (backend nccl = RCCL) and run the step through the N > 1 code "
                          "path (SM_DIST_SINGLE_RANK=1): every collective of the distributed step executes through RCCL on this GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run every other measurement: the other layout, the GEMM roofline, the measured "
+                         "peaks, the sparse-regime / configs[4] / sequence-sweep legs, the CPU baseline and, at N > 1, the score exchange "
+                         "(a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, sampled sparse representations and parameters, IDF) as "
+                         "DIR/<name>.npy, float32 / float64, rank 0")
     return ap.parse_args()
 
 
@@ -612,6 +626,39 @@ def c5_leg(timeout_s=240):
         return {"error": f"{type(e).__name__}: {e}"}
 
 
+DUMP_SEED = 20240607  # fixed: the same elements are sampled in every run, so two builds compare output for output
+
+
+def dump_outputs(trainer, ranking, total, out_dir):
+    """--dump-outputs: what the timed path handed its caller in its LAST timed step -- the step's losses (and those of every
+    timed step), the sparse document representations it computed and the parameters its optimiser step left (a fixed, seeded
+    sample of each of the two large arrays), the trained IDF vector.  float64 for the losses, float32 otherwise; ~25 MB."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    sm = trainer.model.sparse_model
+    g = torch.Generator().manual_seed(DUMP_SEED)
+
+    def sample(t, n):
+        flat = t.detach().reshape(-1)
+        if flat.numel() <= n:
+            return flat.float().cpu().numpy()
+        idx = torch.randint(0, flat.numel(), (n,), generator=g).to(flat.device)
+        return flat[idx].float().cpu().numpy()
+
+    arrays = {
+        "loss_total": np.array([total[-1]], dtype=np.float64),
+        "loss_ranking": np.array([ranking[-1]], dtype=np.float64),
+        "losses_total_per_step": np.array(total, dtype=np.float64),
+        "losses_ranking_per_step": np.array(ranking, dtype=np.float64),
+        "d_rep_sample": sample(trainer._last["d_rep"], 1 << 21),
+        "params_sample": sample(sm.backbone.flat_param, 1 << 22),
+        "idf": sm.idf_vector.detach().float().cpu().numpy(),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if os.environ.get("SM_FAULTHANDLER_S"):  # tests: a stalled rank prints every thread's stack and exits instead of hanging
@@ -647,15 +694,17 @@ def main():
         from sparse_hip import lib as _L
         _L._LIB_PATH = os.environ['SM_LIB']
     from sparse_hip import ops
+    torch.manual_seed(0)  # identical inputs run to run (--dump-outputs compares builds); the workload draws from seeded generators anyway
     other = "dense" if args.layout == "ragged" else "ragged"
-    trainer, cfg, batches = build_trainer(args, device, rank, layouts=(args.layout,) if args.only_value_layout else (args.layout, other))
+    both = args.full and not args.only_value_layout  # the other layout is timed by --full only
+    trainer, cfg, batches = build_trainer(args, device, rank, layouts=(args.layout, other) if both else (args.layout,))
 
     def barrier():
         if dist_on:
             dist.barrier()
         torch.cuda.synchronize()
 
-    live = {}
+    live, step_losses = {}, {}
 
     def timed(layout, kt=None):
         """W untimed + exactly K timed steps bracketed by barrier + synchronize; max over ranks.  The loss of every timed step
@@ -677,6 +726,7 @@ def main():
         bb_ = trainer.model.sparse_model.backbone
         ls = [float(x) for x in torch.stack([l.reshape(()) for l in losses]).float().cpu()]
         tt = [float(x) for x in torch.stack([l.reshape(()) for l in totals]).float().cpu()]
+        step_losses[layout] = (ls, tt)
         live[layout] = {"loss_first": ls[0], "loss_last": ls[-1], "loss_min": min(ls), "loss_max": max(ls), "total_loss_first": tt[0],
                         "total_loss_last": tt[-1], "distinct_losses": len(set(ls)),
                         "finite": bool(all(l == l and abs(l) != float("inf") for l in ls)) and bool(torch.isfinite(bb_.flat_param).all())
@@ -694,12 +744,18 @@ def main():
     env_exchange = os.environ.get("SM_EXCHANGE")
     if dist_on:
         os.environ["SM_EXCHANGE"] = "gather"
-    with KernelTimer(ops, "sparse_head_fwd") as kt:
-        elapsed = timed(args.layout, kt)   # <- the line's `value`
-        head_ms = kt.mean_ms()
-        rows = list(kt.rows)
+    head_ms, rows = None, []
+    if args.full:  # HIP events around every head-forward launch of the timed steps (roofline_head_fwd)
+        with KernelTimer(ops, "sparse_head_fwd") as kt:
+            elapsed = timed(args.layout, kt)   # <- the line's `value`
+            head_ms = kt.mean_ms()
+            rows = list(kt.rows)
+    else:
+        elapsed = timed(args.layout)           # <- the line's `value`
+    if args.dump_outputs and rank == 0:  # before anything else runs a step: the outputs of the last TIMED step
+        dump_outputs(trainer, *step_losses[args.layout], args.dump_outputs)
     elapsed_scores = None
-    if dist_on:
+    if dist_on and args.full:
         os.environ["SM_EXCHANGE"] = "scores"
         try:
             elapsed_scores = timed(args.layout)
@@ -708,9 +764,9 @@ def main():
             os.environ["SM_EXCHANGE"] = "gather"
         live[args.layout] = None
         elapsed_again = timed(args.layout)  # liveness record of the value layout in gather mode again (and a second gather sample)
-    elapsed_other = float("nan") if args.only_value_layout else timed(other)  # the other layout, outside the headline region
-    gemm_lines = gemm_lines_serial = None
-    if world == 1 and not single and not args.no_gemm_roofline:  # outside the timed region: does not touch `value`
+    elapsed_other = timed(other) if both else float("nan")  # the other layout, outside the headline region
+    gemm_lines = gemm_lines_serial = other_clock_lines = other_clock_serial = None
+    if args.full and world == 1 and not single and not args.no_gemm_roofline:  # outside the timed region: does not touch `value`
         with GemmRoofline(ops) as gr:
             bs_ = batches[args.layout]
             for i in range(3):
@@ -737,14 +793,7 @@ def main():
 
     k = args.negs + 1
     T_padded = args.bs * k * args.seq
-    T = sum(rows) / max(1, len(rows))  # rows per launch: the ragged layout skips padding tokens
-    H, V = cfg.hidden_size, cfg.vocab_size
-    head_flops = 2.0 * T * H * V  # executed FLOPs of one fused decoder launch (2THV, T = computed rows)
-    achieved = head_flops / (head_ms * 1e-3)
-    peak = MFMA_PEAK[args.dtype]
-    traffic, traffic_src, traffic_git, traffic_kernel = None, None, None, None
-    if args.bs == 32 and args.negs == 15 and args.seq == 128 and args.dtype == "bf16":
-        traffic, traffic_src, traffic_git, traffic_kernel = latest_traffic(HEAD_KERNELS, args.layout)
+    T = sum(rows) / max(1, len(rows))  # rows per launch: the ragged layout skips padding tokens (--full: counted by the head timer)
     sps = lambda el: world * args.bs * args.steps / el
     result = {
         "metric": "training samples/sec (q+1pos+15neg, seq128)",
@@ -765,8 +814,8 @@ def main():
                                f"bs={args.bs} x (1 pos + {args.negs} negs), seq {args.seq}, inference-free queries, "
                                "InfoNCE in-batch negatives + FLOPS, dropout " + ("off" if args.no_dropout else "0.1") + ", fused AdamW" + (", fp32 residual stream (bf16 GEMM operands)" if not args.bf16_storage else ", all-bf16 activation storage") + "; "
                                f"documents (lengths ~N(80,30) in [16,{args.seq}]) padded to {args.seq} by the collator; `value` is the "
-                               + (f"ragged layout: padding tokens skipped on the device ({T:.0f} of {T_padded} token rows computed per step, "
-                                  "identical outputs); value_dense_layout computes all of them" if args.layout == "ragged" else
+                               + ("ragged layout: padding tokens skipped on the device (" + (f"{T:.0f} of {T_padded} token rows computed per step, " if rows else "")
+                                  + "identical outputs); value_dense_layout computes all of them" if args.layout == "ragged" else
                                   f"dense layout: all {T_padded} token rows computed (attention skips key tiles that hold only masked keys: exact); value_ragged_layout skips padding tokens"),
                    "global_batch": world * args.bs, "docs_per_query": k, "seq_len": args.seq,
                    "parallelism": f"dp{world}" + ("" if world == 1 else " (in-batch negatives across ranks over RCCL; `value`: exchange mode "
@@ -775,6 +824,8 @@ def main():
                                                       "queries (under the document encoder) and of the score blocks + all-reduce of the FLOPS "
                                                       "column means; both: flat-gradient all-reduce in slices overlapped with backward)")},
     }
+    if not args.full:  # a plain run times the value layout only
+        del result[f"value_{other}_layout"]
     if single:
         result["single_rank_rccl"] = ("the step through the N > 1 code path with a process group of ONE rank (SM_DIST_SINGLE_RANK=1): every collective "
                                       "of the distributed step (query all-gather on the communication stream, loss-head exchange, slice-wise gradient "
@@ -785,12 +836,38 @@ def main():
             ver = ".".join(str(x) for x in torch.cuda.nccl.version())
         except Exception as e:  # noqa: BLE001  (a build without the binding: say so instead of failing the run)
             ver = f"unavailable ({type(e).__name__})"
-        result["value_scores_exchange"] = sps(elapsed_scores)
-        result["ms_per_step_scores_exchange"] = elapsed_scores / args.steps * 1e3
-        result["value_gather_second_sample"] = sps(elapsed_again)
+        if args.full:
+            result["value_scores_exchange"] = sps(elapsed_scores)
+            result["ms_per_step_scores_exchange"] = elapsed_scores / args.steps * 1e3
+            result["value_gather_second_sample"] = sps(elapsed_again)
         result["dist"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "rccl_version": ver,
-                          "exchange": "gather (value), scores (value_scores_exchange)", "exchange_env_at_start": env_exchange, "gpus_visible": ndev,
+                          "exchange": "gather (value), scores (value_scores_exchange)" if args.full else "gather (value)",
+                          "exchange_env_at_start": env_exchange, "gpus_visible": ndev,
                           "env": {k: os.environ[k] for k in ("NCCL_DEBUG", "HSA_ENABLE_IPC_MODE_LEGACY", "NCCL_ALGO", "NCCL_PROTO") if k in os.environ}}
+    if args.full:
+        full_records(args, result, trainer, batches, device, world, single, rank, elapsed, elapsed_other, T, head_ms, cfg,
+                     gemm_lines, gemm_lines_serial, other_clock_lines, other_clock_serial)
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    if dist_on:
+        dist.barrier()
+        dist.destroy_process_group()
+    if not result["finite"]:
+        print("bench.py: the timed region did not train (non-finite parameters / losses, or a loss that does not move): " + json.dumps(live),
+              file=sys.stderr)
+        sys.exit(3)
+
+
+def full_records(args, result, trainer, batches, device, world, single, rank, elapsed, elapsed_other, T, head_ms, cfg,
+                 gemm_lines, gemm_lines_serial, other_clock_lines, other_clock_serial):
+    """--full: the records beside `value` (all measured outside the headline's timed region)"""
+    H, V = cfg.hidden_size, cfg.vocab_size
+    head_flops = 2.0 * T * H * V  # executed FLOPs of one fused decoder launch (SURVEY 8d: 2THV, T = computed rows)
+    achieved = head_flops / (head_ms * 1e-3)
+    peak = MFMA_PEAK[args.dtype]
+    traffic, traffic_src, traffic_git, traffic_kernel = None, None, None, None
+    if args.bs == 32 and args.negs == 15 and args.seq == 128 and args.dtype == "bf16":
+        traffic, traffic_src, traffic_git, traffic_kernel = latest_traffic(HEAD_KERNELS, args.layout)
     head_line = {"kernel": "fused MLM decoder + seq-max + log1p(relu) (sm_sparse_head_fwd)", "bound": "mfma",
                  "achieved": achieved / 1e12, "peak": peak / 1e12, "unit": "TFLOP/s", "frac": achieved / peak,
                  "traffic": traffic, "traffic_unit": "bytes/launch (HBM-side reads x2-corrected + writes)", "traffic_source": traffic_src,
@@ -851,14 +928,6 @@ def main():
                 hv["frac_of_measured_copy_rate"] = hv["achieved"] / pm["hbm_copy_gbs"]
         if world == 1 and not single and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args)
-        print(json.dumps(result), flush=True)
-    if dist_on:
-        dist.barrier()
-        dist.destroy_process_group()
-    if not result["finite"]:
-        print("bench.py: the timed region did not train (non-finite parameters / losses, or a loss that does not move): " + json.dumps(live),
-              file=sys.stderr)
-        sys.exit(3)
 
 
 if __name__ == "__main__":

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,11 +49,12 @@ def test_cli_defaults_follow_the_measurement_protocol():
     assert a.gpus == 1 and a.steps >= 50 and a.warmup >= 10
     assert a.layout == "dense"            # the headline computes every padded token row; the ragged rate is reported beside it
     assert not a.cpu_baseline_bounded     # the CPU leg runs configs[1] at full shape by default
+    assert not a.full and a.dump_outputs is None  # a plain run times the headline only; --full adds every other record
 
 
 @pytest.mark.gpu
 def test_bench_one_gpu_line():
-    r = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu-baseline"], timeout=540)
+    r = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--full"], timeout=540)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     j = _line(r.stdout)
     # the two records that ride beside `value` (round 5): the step at ~1 % live activations, configs[4]'s per-GPU shape on one GPU
@@ -85,13 +87,39 @@ def test_bench_one_gpu_line():
 
 
 @pytest.mark.gpu
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """a plain run (no --full) times exactly --steps steps and prints the headline fields only; --dump-outputs writes what the last
+    timed step computed, float32 / float64, within 64 MB, and two runs with the same arguments are fed identical inputs"""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)],
+                 timeout=300)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        j = _line(r.stdout)
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "finite"} <= set(j), j
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["finite"] is True and j["dtype"] == "bf16"
+        assert abs(j["value"] - 32 * 3 / (j["ms_per_step"] * 3e-3)) < 1e-6 * j["value"]
+        assert not {"roofline", "cpu_baseline", "sparse_regime", "c5_per_gpu", "seq_sweep", "value_ragged_layout"} & set(j), sorted(j)
+        files = sorted(d.glob("*.npy"))
+        assert {f.stem for f in files} >= {"loss_total", "d_rep_sample", "params_sample"}, files
+        arrs = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        assert len(arrs["losses_total_per_step"]) == 3 and arrs["loss_total"][0] == arrs["losses_total_per_step"][-1]
+        dumps.append(arrs)
+    # identical inputs and initial weights: the first timed step's losses agree closely between the runs
+    assert np.allclose(dumps[0]["losses_total_per_step"][0], dumps[1]["losses_total_per_step"][0], rtol=1e-3, atol=1e-3)
+
+
+@pytest.mark.gpu
 def test_bench_two_ranks_on_one_gpu_over_gloo():
     """the N > 1 launch contract (RANK / LOCAL_RANK / WORLD_SIZE from torch.distributed.run, barrier + max over ranks, one line
     from rank 0); RCCL needs one GPU per rank, so on the single test GPU the transport is gloo (SM_BENCH_BACKEND)"""
     env = dict(os.environ, SM_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2", SM_FAULTHANDLER_S="240")
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
               "127.0.0.1", "--master-port", "29591", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-              "--warmup", "1"], env=env, timeout=420)
+              "--warmup", "1", "--full"], env=env, timeout=420)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     j = _line(r.stdout)
     assert j["n_gpus"] == 2 and j["config"]["global_batch"] == 64 and j["scaling"] == "weak"
@@ -107,7 +135,8 @@ def test_bench_two_ranks_on_one_gpu_over_gloo():
 def test_bench_single_rank_rccl_line():
     """bench.py --single-rank-rccl: the N > 1 code path through RCCL with a communicator of one rank (the only RCCL execution a
     one-GPU box allows): both exchange modes timed, the dist record names the backend and the RCCL version"""
-    r = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--single-rank-rccl", "--steps", "4", "--warmup", "2"], timeout=420)
+    r = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--single-rank-rccl", "--steps", "4", "--warmup", "2", "--full"],
+             timeout=420)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     j = _line(r.stdout)
     assert j["n_gpus"] == 1 and j["finite"] is True and j["value"] > 0
