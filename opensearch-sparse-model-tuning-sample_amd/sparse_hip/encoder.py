@@ -166,6 +166,39 @@ def param_layout(cfg: BertConfigLite) -> List[Tuple[str, Tuple[int, ...]]]:
     return out
 
 
+# Attribute -> HF name(s) below the handle's prefix.  A tuple is a LayerNorm's (gamma, beta); a list names adjacent equal tensors
+# that one view spans (the fused QKV weight [3H, H] and bias [3H]).
+_EMB_FIELDS = {"word": "word_embeddings.weight", "pos": "position_embeddings.weight", "type": "token_type_embeddings.weight",
+               "ln": ("LayerNorm.weight", "LayerNorm.bias")}
+_LAYER_FIELDS = {"qkv_w": ["attention.self.query.weight", "attention.self.key.weight", "attention.self.value.weight"],
+                 "qkv_b": ["attention.self.query.bias", "attention.self.key.bias", "attention.self.value.bias"],
+                 "o_w": "attention.output.dense.weight", "o_b": "attention.output.dense.bias",
+                 "ln1": ("attention.output.LayerNorm.weight", "attention.output.LayerNorm.bias"),
+                 "w1_w": "intermediate.dense.weight", "w1_b": "intermediate.dense.bias",
+                 "w2_w": "output.dense.weight", "w2_b": "output.dense.bias",
+                 "ln2": ("output.LayerNorm.weight", "output.LayerNorm.bias")}
+_HEAD_FIELDS = {"t_w": "transform.dense.weight", "t_b": "transform.dense.bias",
+                "ln": ("transform.LayerNorm.weight", "transform.LayerNorm.bias"), "bias": "bias"}
+
+
+class _Params:
+    """The tensors of one layer (of the embeddings, of the head) by attribute, as views of the flat parameter buffer; `.grad` is
+    the same handle over the flat gradient buffer.  `names`: attribute -> the layout names it reaches."""
+
+    def __init__(self, model: "HipBertMLM", prefix: str, fields: dict, grad: bool = False):
+        self.names = {attr: [prefix + n for n in ([spec] if isinstance(spec, str) else spec)] for attr, spec in fields.items()}
+        buf = model.flat_grad if grad else model.flat_param
+        for attr, names in self.names.items():
+            if isinstance(fields[attr], list):
+                (o0, shape), (o1, _) = model._offsets[names[0]], model._offsets[names[-1]]
+                val = buf[o0:o1 + int(math.prod(shape))].view((len(names) * shape[0],) + tuple(shape[1:]))
+            else:
+                views = tuple(model.view(n, grad) for n in names)
+                val = views if isinstance(fields[attr], tuple) else views[0]
+            setattr(self, attr, val)
+        self.grad = None if grad else _Params(model, prefix, fields, grad=True)
+
+
 def _attach(root: torch.nn.Module, dotted: str, param: torch.nn.Parameter) -> None:
     mod = root
     parts = dotted.split(".")
@@ -178,6 +211,22 @@ def _attach(root: torch.nn.Module, dotted: str, param: torch.nn.Parameter) -> No
 
 class _Site:
     EMB, ATTN, HID1, HID2 = 0, 1, 2, 3
+
+
+class _FFN:
+    """which feed-forward forward a layer took, i.e. what its record holds for the backward:
+    FUSED  ffn_pc_fwd: f1 tile-major (4 dims), gelu(f1) not kept
+    F16    fp16 operands: f1 row-major in bf16, gelu(f1) kept in fp16 only and so not saved
+    PLAIN  f1 row-major and ga = gelu(f1) (also the fp8 GELU + quantise pass, whose f1 is the pre-activation as well)"""
+    FUSED, F16, PLAIN = 0, 1, 2
+
+
+# What a forward with grad keeps for its backward.  A layer's record: its thirteen activations, the feed-forward form that made
+# them (_FFN) and the layer's dropout descriptors (None: no dropout) -- the backward re-draws the forward's masks from those.
+_EmbSaved = collections.namedtuple("_EmbSaved", "z0 m0 r0 d_emb")
+_LayerSaved = collections.namedtuple("_LayerSaved", "x qkv ctx lse z1 m1 r1 x1 f1 ga z2 m2 r2 form d_at d_h1 d_h2")
+_HeadSaved = collections.namedtuple("_HeadSaved", "x ft gt mt rt tn rep argmax")
+_Meta = collections.namedtuple("_Meta", "ids mask B S use_l0 rag")
 
 
 # Kernel-selection switches of HipBertMLM that are not numerics choices (those are constructor arguments of their own: residual_fp32,
@@ -214,6 +263,16 @@ def _kernel_option(explicit: Optional[dict], name: str):
 
 class HipBertMLM(torch.nn.Module):
     """BertForMaskedLM-shaped module whose math runs in libsparse_hip.so."""
+
+    _layer_hook = None
+    check_finite = False  # TrainingArguments.check_finite / SM_CHECK_FINITE: also look for fp16 operand overflow in the forward
+    _dropout_without_grad = False
+    _cast_table = _cast_key = _cast_table16 = _cast_key16 = None
+    _small_ffn16 = False
+    _handle_cache = _handle_key = None
+    _x_last_f16 = None
+    _wgrad = None
+    _argmax_log = None
 
     def __init__(self, cfg: BertConfigLite, compute_dtype: torch.dtype = torch.bfloat16,
                  device: Optional[torch.device] = None, init_seed: Optional[int] = 0, with_head: bool = True,
@@ -339,20 +398,20 @@ class HipBertMLM(torch.nn.Module):
         n = int(math.prod(shape))
         return (self.flat_grad if grad else self.flat_param)[o:o + n].view(shape)
 
-    def _span(self, first: str, last: str, grad: bool, shape) -> Tensor:
-        o0, _ = self._offsets[first]
-        o1, s1 = self._offsets[last]
-        buf = self.flat_grad if grad else self.flat_param
-        return buf[o0:o1 + int(math.prod(s1))].view(shape)
+    def _handles(self) -> Tuple[_Params, List[_Params], _Params]:
+        """(embeddings, [layer 0, ...], head) parameter handles.  Cached: building them for 6 layers took 2 ms of host time
+        (164 views) where a whole step's enqueue takes 4.3-4.8 ms and every forward and backward asks for them; the views alias
+        the flat buffers, so the cache goes stale only if a buffer moves."""
+        key = (self.flat_param.data_ptr(), self.flat_grad.data_ptr())
+        if self._handle_key != key:
+            layers = [_Params(self, f"bert.encoder.layer.{l}.", _LAYER_FIELDS) for l in range(self.config.num_hidden_layers)]
+            self._handle_cache = (_Params(self, "bert.embeddings.", _EMB_FIELDS), layers, _Params(self, "cls.predictions.", _HEAD_FIELDS))
+            self._handle_key = key
+        return self._handle_cache
 
     def qkv_weight(self, l: int, grad: bool = False) -> Tensor:
-        p = f"bert.encoder.layer.{l}.attention.self."
-        H = self.config.hidden_size
-        return self._span(p + "query.weight", p + "value.weight", grad, (3 * H, H))
-
-    def qkv_bias(self, l: int, grad: bool = False) -> Tensor:
-        p = f"bert.encoder.layer.{l}.attention.self."
-        return self._span(p + "query.bias", p + "value.bias", grad, (3 * self.config.hidden_size,))
+        h = self._handles()[1][l]
+        return (h.grad if grad else h).qkv_w
 
     def reset_parameters(self, seed: int = 0, std: float = 0.02) -> None:
         """HF-style init: N(0, 0.02) weights, zero biases, LN weight 1 (generated on the host)."""
@@ -465,23 +524,25 @@ class HipBertMLM(torch.nn.Module):
         cfg, dt, dev = self.config, self.compute_dtype, self.device
         H, I, V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
         st = self._staged
+        vpad = (V + 127) // 128 * 128
 
-        def buf(key, shape):
+        def buf(key, shape, dtype=dt):
             if key not in st:
-                st[key] = torch.zeros(shape, dtype=dt, device=dev)
+                st[key] = torch.zeros(shape, dtype=dtype, device=dev)
             return st[key]
 
         key = (self.flat_param.data_ptr(), len(st))
-        if self._cast_table is None or self._cast_key != key:
-            vpad = (V + 127) // 128 * 128
-            ent = [(self.view("bert.embeddings.word_embeddings.weight"), buf("E", (vpad, H)), None)]
-            for l in range(cfg.num_hidden_layers):
-                p = f"bert.encoder.layer.{l}."
-                ent.append((self.qkv_weight(l), buf(f"qkv{l}", (3 * H, H)), buf(f"qkvT{l}", (H, 3 * H))))
-                ent.append((self.view(p + "attention.output.dense.weight"), buf(f"o{l}", (H, H)), buf(f"oT{l}", (H, H))))
-                ent.append((self.view(p + "intermediate.dense.weight"), buf(f"w1{l}", (I, H)), buf(f"w1T{l}", (H, I))))
-                ent.append((self.view(p + "output.dense.weight"), buf(f"w2{l}", (H, I)), buf(f"w2T{l}", (I, H))))
-            ent.append((self.view("cls.predictions.transform.dense.weight"), buf("t", (H, H)), buf("tT", (H, H))))
+        if self._cast_key != key:
+            self._cast_table = self._handle_key = None  # raw pointers, and views of the same buffer: both are made anew
+        emb, layers, head = self._handles()
+        if self._cast_table is None:
+            ent = [(emb.word, buf("E", (vpad, H)), None)]
+            for l, P in enumerate(layers):
+                ent.append((P.qkv_w, buf(f"qkv{l}", (3 * H, H)), buf(f"qkvT{l}", (H, 3 * H))))
+                ent.append((P.o_w, buf(f"o{l}", (H, H)), buf(f"oT{l}", (H, H))))
+                ent.append((P.w1_w, buf(f"w1{l}", (I, H)), buf(f"w1T{l}", (H, I))))
+                ent.append((P.w2_w, buf(f"w2{l}", (H, I)), buf(f"w2T{l}", (I, H))))
+            ent.append((head.t_w, buf("t", (H, H)), buf("tT", (H, H))))
             self._cast_table = ops.CastTable(ent)  # raw pointers: rebuilt if the flat buffer or the staging set changes
             self._cast_key = (self.flat_param.data_ptr(), len(st))
         self._cast_table.run()
@@ -491,18 +552,12 @@ class HipBertMLM(torch.nn.Module):
             ffn16 = self.ffn_fwd_f16 or (self.pc_ffn and self.ffn_f16 and self._small_ffn16)
             key16 = (self.flat_param.data_ptr(), ffn16)
             if self._cast_table16 is None or self._cast_key16 != key16:
-                def buf16(k, shape):
-                    if k not in st:
-                        st[k] = torch.zeros(shape, dtype=torch.float16, device=dev)
-                    return st[k]
-                vpad = (V + 127) // 128 * 128
-                ent = [(self.view("bert.embeddings.word_embeddings.weight"), buf16("E16", (vpad, H)), None),
-                       (self.view("cls.predictions.transform.dense.weight"), buf16("t16", (H, H)), None)]
+                f16 = torch.float16
+                ent = [(emb.word, buf("E16", (vpad, H), f16), None), (head.t_w, buf("t16", (H, H), f16), None)]
                 if ffn16:
-                    for l in range(cfg.num_hidden_layers):
-                        p = f"bert.encoder.layer.{l}."
-                        ent.append((self.view(p + "intermediate.dense.weight"), buf16(f"w1h{l}", (I, H)), None))
-                        ent.append((self.view(p + "output.dense.weight"), buf16(f"w2h{l}", (H, I)), None))
+                    for l, P in enumerate(layers):
+                        ent.append((P.w1_w, buf(f"w1h{l}", (I, H), f16), None))
+                        ent.append((P.w2_w, buf(f"w2h{l}", (H, I), f16), None))
                 self._cast_table16 = ops.CastTable(ent)
                 self._cast_key16 = key16
             self._cast_table16.run()
@@ -515,11 +570,8 @@ class HipBertMLM(torch.nn.Module):
                 if self.pc_ffn_bwd:  # the backward's operands (bf16)
                     st["pc_w2tf"] = torch.empty((nl, I // 32, 24, 64, 8), dtype=torch.bfloat16, device=dev)
                     st["pc_w1tf"] = torch.empty((nl, I // 32, 24, 64, 8), dtype=torch.bfloat16, device=dev)
-            n0 = "bert.encoder.layer.0."
-            stride = (self._offsets["bert.encoder.layer.1.intermediate.dense.weight"][0]
-                      - self._offsets[n0 + "intermediate.dense.weight"][0]) if nl > 1 else 0
-            ops.ffn_pc_stage(self.view(n0 + "intermediate.dense.weight"), self.view(n0 + "output.dense.weight"), stride, nl,
-                             st["pc_w1f"], st["pc_w2f"], st.get("pc_w2tf"), st.get("pc_w1tf"))
+            stride = layers[1].w1_w.storage_offset() - layers[0].w1_w.storage_offset() if nl > 1 else 0  # elements, layer to layer
+            ops.ffn_pc_stage(layers[0].w1_w, layers[0].w2_w, stride, nl, st["pc_w1f"], st["pc_w2f"], st.get("pc_w2tf"), st.get("pc_w1tf"))
         if self.fp8:  # e4m3 copies of the encoder linears' weights (and of their transposes, for the input gradients) + scales
             for l in range(cfg.num_hidden_layers):
                 for k in ("qkv", "o", "w1", "w2"):
@@ -538,38 +590,42 @@ class HipBertMLM(torch.nn.Module):
             self._fp8_cur, self._fp8_next = (torch.zeros(n, dtype=torch.float32, device=device) for _ in range(2))
         return self._fp8_sites.setdefault(key, len(self._fp8_sites))
 
-    def _lin(self, a, key: str, grad: bool = False, emit8: Optional[str] = None, keep16: bool = True, emit8_grad: bool = False, **epi):
-        """epilogue(a . W^T) for the staged weight `key` of an encoder linear: bf16 / fp32 operands, or (self.fp8) `a` quantised here
-        to e4m3 (e5m2 when it is a gradient) against the staged e4m3 weight.  emit8 = the key of the linear that consumes the result
-        (fp8 mode with delayed scaling, once that site has a history): the GEMM's epilogue writes the fp8 operand itself -- no
-        separate quantisation pass over the [T, N] result -- and the return value is (out, (q, scale)) where `a` of the consumer's
-        _lin call may be that pair; keep16 = False: the 16-bit result is not written at all (out is None)"""
+    def _lin(self, a, key: str, grad: bool = False, **epi) -> Tensor:
+        """epilogue(a . W^T) for the staged weight `key` of an encoder linear: bf16 / fp32 operands, or (self.fp8) `a` quantised
+        to e4m3 (e5m2 when it is a gradient: grad) against the staged e4m3 weight; `a` may be the (q, scale) pair _lin_emit returned"""
+        return self._lin_emit(a, key, None, grad, **epi)[0]
+
+    def _lin_emit(self, a, key: str, consumer: Optional[str], grad: bool = False, keep16: bool = True, **epi):
+        """(out, q8) of _lin where the result feeds the linear `consumer`: with fp8_emit (fp8 mode with delayed scaling, once that
+        site has a history) the GEMM's epilogue writes the consumer's fp8 operand itself -- no separate quantisation pass over the
+        [T, N] result -- and q8 = (q, scale); otherwise q8 is None.  keep16 = False: with q8, the 16-bit result is not written at
+        all (out is None)"""
         st = self._staged
         q8 = None
-        if emit8 is not None and self.fp8 and self._fp8_delayed and self.fp8_emit:
-            j = self._fp8_site(emit8, st[key].device)
+        if consumer is not None and self.fp8 and self._fp8_delayed and self.fp8_emit:
+            j = self._fp8_site(consumer, st[key].device)
             if j in self._fp8_ready:
-                q8 = (self._fp8_cur[j:j + 1], self._fp8_next[j:j + 1], emit8_grad)  # (a gradient operand is e5m2)
+                q8 = (self._fp8_cur[j:j + 1], self._fp8_next[j:j + 1], grad)  # (a gradient operand is e5m2)
                 epi = dict(epi, q8=q8, no_out=not keep16)
-        if isinstance(a, tuple):  # an fp8 operand an earlier epilogue produced: (q, scale)
-            aq, sa = a
+        if isinstance(a, tuple) or (self.fp8 and a.dtype == torch.bfloat16):
+            aq, sa = a if isinstance(a, tuple) else self._fp8_operand(a, key, grad)
             r = ops.gemm_nt(aq, st[key + "_8"], scale_a=sa, scale_b=st[key + "_8s"], **epi)
-            return (r[0], (r[1], r[2])) if q8 is not None else ((r, None) if emit8 is not None else r)
-        if self.fp8 and a.dtype == torch.bfloat16:
-            if not self._fp8_delayed:
-                aq, sa, _ = ops.quantize_fp8(a, e5m2=grad)
-            else:
-                i = self._fp8_site(key, a.device)
-                nxt = self._fp8_next[i:i + 1]
-                if i in self._fp8_ready:
-                    aq, sa, _ = ops.quantize_fp8(a, e5m2=grad, amax=self._fp8_cur[i:i + 1], amax_next=nxt)
-                else:  # no history for this site yet: measure now, remember for the next step
-                    aq, sa, am = ops.quantize_fp8(a, e5m2=grad)
-                    torch.maximum(nxt, am, out=nxt)
-            r = ops.gemm_nt(aq, st[key + "_8"], scale_a=sa, scale_b=st[key + "_8s"], **epi)
-            return (r[0], (r[1], r[2])) if q8 is not None else ((r, None) if emit8 is not None else r)
-        r = ops.gemm_nt(a, st[key], **epi)
-        return (r, None) if emit8 is not None else r
+        else:
+            r = ops.gemm_nt(a, st[key], **epi)
+        return (r[0], (r[1], r[2])) if q8 is not None else (r, None)
+
+    def _fp8_operand(self, a: Tensor, key: str, grad: bool):
+        """(q, scale) of `a` as the fp8 operand of the linear `key`: measured just in time, or (delayed scaling) scaled by the
+        maximum the site showed during the previous step while this step's maximum is recorded in the same pass"""
+        if not self._fp8_delayed:
+            return ops.quantize_fp8(a, e5m2=grad)[:2]
+        i = self._fp8_site(key, a.device)
+        nxt = self._fp8_next[i:i + 1]
+        if i in self._fp8_ready:
+            return ops.quantize_fp8(a, e5m2=grad, amax=self._fp8_cur[i:i + 1], amax_next=nxt)[:2]
+        aq, sa, am = ops.quantize_fp8(a, e5m2=grad)  # no history for this site yet: measure now, remember for the next step
+        torch.maximum(nxt, am, out=nxt)
+        return aq, sa
 
     def _fp8_gelu_site(self, consumer_key: str, device):
         """(amax, amax_next) of the fp8 operand site of `consumer_key` when the fused GELU + quantise pass may produce that operand:
@@ -611,14 +667,12 @@ class HipBertMLM(torch.nn.Module):
         A, eps = cfg.num_attention_heads, cfg.layer_norm_eps
         ph, pa = cfg.hidden_dropout_prob, cfg.attention_probs_dropout_prob
         self.sync_weights()
-        st, v = self._staged, self.view
-        e = "bert.embeddings."
-        saved = {"layers": []} if save else None
+        st = self._staged
+        E, layers, _ = self._handles()
+        last = cfg.num_hidden_layers - 1
         d_emb = self._drop(ph, training, seed, 0, _Site.EMB)
         r32 = self.residual_fp32
-        emb = ops.embed_fwd(ids, st["E"], v(e + "position_embeddings.weight"),
-                            v(e + "token_type_embeddings.weight")[0], v(e + "LayerNorm.weight"),
-                            v(e + "LayerNorm.bias"), eps, d_emb, rag, want_y32=r32)
+        emb = ops.embed_fwd(ids, st["E"], E.pos, E.type[0], *E.ln, eps, d_emb, rag, want_y32=r32)
         z0, x, m0, r0 = emb[:4]
         # fp32 residual stream: the residual of a block is the fp32 OUTPUT of the previous LayerNorm.  Only the embedding
         # stores it (x32); inside the layers the consuming GEMM epilogue recomputes it from that LayerNorm's stored fp32
@@ -626,17 +680,15 @@ class HipBertMLM(torch.nn.Module):
         x32 = emb[4] if r32 else None
         res_ln = None  # (mean, rstd, gamma, beta) of the LayerNorm whose fp32 input x32 currently holds
         xh_last = None  # fp16 copy of the last layer's output (fwd_f16: operand of the head transform)
-        if save:
-            saved["emb"] = (z0, m0, r0)
-        for l in range(cfg.num_hidden_layers):
-            p = f"bert.encoder.layer.{l}."
+        emb_saved = _EmbSaved(z0, m0, r0, d_emb) if save else None
+        saved = [] if save else None  # one _LayerSaved per layer
+        for l, P in enumerate(layers):
             d_at = self._drop(pa, training, seed, l + 1, _Site.ATTN)
             d_h1 = self._drop(ph, training, seed, l + 1, _Site.HID1)
             d_h2 = self._drop(ph, training, seed, l + 1, _Site.HID2)
-            qkv = self._lin(x, f"qkv{l}", bias=self.qkv_bias(l))
+            qkv = self._lin(x, f"qkv{l}", bias=P.qkv_b)
             ctx, lse = ops.attention_fwd(qkv, mask, B, S, A, d_at, rag)
-            z1 = self._lin(ctx, f"o{l}", bias=v(p + "attention.output.dense.bias"), drop=d_h1, residual=x32 if r32 else x, out_f32=r32,
-                             residual_ln=res_ln)
+            z1 = self._lin(ctx, f"o{l}", bias=P.o_b, drop=d_h1, residual=x32 if r32 else x, out_f32=r32, residual_ln=res_ln)
             fused = None
             # (a no-grad forward of fewer than pc_infer_min_rows token rows takes the unfused launches: one fused workgroup walks all
             # of W1 / W2 for its 128 rows -- 69 us per layer however few rows there are -- where the plain GEMMs spread the columns
@@ -644,17 +696,15 @@ class HipBertMLM(torch.nn.Module):
             # ONLY inference takes that detour: a training-mode forward without grad is pass 1 of rep-level gradient caching, which
             # pass 2 (grad on, fused kernel, sigmoid-form GELU) must replay bit for bit
             if self.pc_ffn and z1.shape[0] % 16 == 0 and (save or training or z1.shape[0] >= self.pc_infer_min_rows):
-                g1, b1 = v(p + "attention.output.LayerNorm.weight"), v(p + "attention.output.LayerNorm.bias")
-                g2, b2 = v(p + "output.LayerNorm.weight"), v(p + "output.LayerNorm.bias")
-                fused = ops.ffn_pc_fwd(z1, g1, b1, eps, st["pc_w1f"][l], v(p + "intermediate.dense.bias"), st["pc_w2f"][l],
-                                       v(p + "output.dense.bias"), g2, b2, d_h2, save_f1=save)  # None: shape declined -> unfused launches
+                fused = ops.ffn_pc_fwd(z1, *P.ln1, eps, st["pc_w1f"][l], P.w1_b, st["pc_w2f"][l], P.w2_b, *P.ln2, d_h2,
+                                       save_f1=save)  # None: shape declined -> unfused launches
             if fused is not None:
                 x1, m1, r1, f1, z2, x2, m2, r2 = fused  # f1 tile-major (4 dims): the backward's dF1 epilogue reads it that way
-                x32, res_ln = z2, (m2, r2, g2, b2)
-                if self.fwd_f16 and l == cfg.num_hidden_layers - 1:  # the head transform's fp16 operand
-                    xh_last = ops.layernorm_fwd_res32(z2, g2, b2, eps, x.dtype, want_y32=False, want_y16=True)[4]
+                x32, res_ln = z2, (m2, r2, *P.ln2)
+                if self.fwd_f16 and l == last:  # the head transform's fp16 operand
+                    xh_last = ops.layernorm_fwd_res32(z2, *P.ln2, eps, x.dtype, want_y32=False, want_y16=True)[4]
                 if save:
-                    saved["layers"].append((x, qkv, ctx, lse, z1, m1, r1, x1, f1, None, z2, m2, r2))
+                    saved.append(_LayerSaved(x, qkv, ctx, lse, z1, m1, r1, x1, f1, None, z2, m2, r2, _FFN.FUSED, d_at, d_h1, d_h2))
                 x = x2
                 continue
             # fp16 feed-forward operands: where the model asks for them, and in the small no-grad forwards that bypass the fused
@@ -666,51 +716,49 @@ class HipBertMLM(torch.nn.Module):
                 self._small_ffn16 = True
                 self._weights_dirty = True
                 self.sync_weights()
-            x1h = None
             if r32:
-                g1, b1 = v(p + "attention.output.LayerNorm.weight"), v(p + "attention.output.LayerNorm.bias")
-                ln1 = ops.layernorm_fwd_res32(z1, g1, b1, eps, x.dtype, want_y32=False, want_y16=f16_ffn)
+                ln1 = ops.layernorm_fwd_res32(z1, *P.ln1, eps, x.dtype, want_y32=False, want_y16=f16_ffn)
                 x1, _, m1, r1 = ln1[:4]
                 x1h = ln1[4] if f16_ffn else None
-                res1, res1_ln = z1, (m1, r1, g1, b1)
+                res1, res1_ln = z1, (m1, r1, *P.ln1)
             else:
-                x1, m1, r1 = ops.layernorm_fwd(z1, v(p + "attention.output.LayerNorm.weight"),
-                                               v(p + "attention.output.LayerNorm.bias"), eps)
+                x1, m1, r1 = ops.layernorm_fwd(z1, *P.ln1, eps)
                 res1, res1_ln = x1, None
+            # the FFN-down epilogue, whichever operands it runs on (fp16 operands imply the fp32 residual stream)
+            down = dict(bias=P.w2_b, drop=d_h2, residual=res1, out_f32=r32, residual_ln=res1_ln)
             gsite = None if f16_ffn else self._fp8_gelu_site(f"w2{l}", x1.device)
             f1 = torch.empty((x1.shape[0], cfg.intermediate_size), dtype=x1.dtype, device=x1.device) if save and gsite is None else None
             if gsite is not None:
                 # fp8, bert-base width: the GELU epilogue is vector-bound (978 us against 470 us for the plain product at 160 k rows), so
                 # the product goes through the weight-stationary kernel with its bias and ONE pass makes gelu(f1) and its e4m3 copy
-                pre = self._lin(x1, f"w1{l}", bias=v(p + "intermediate.dense.bias"))
+                pre = self._lin(x1, f"w1{l}", bias=P.w1_b)
                 ga, gq, gs = ops.gelu_quantize_fp8(pre, gsite[0], gsite[1], want16=save)
                 f1 = pre if save else None
-                z2 = self._lin((gq, gs), f"w2{l}", bias=v(p + "output.dense.bias"), drop=d_h2, residual=res1, out_f32=r32, residual_ln=res1_ln)
+                z2 = self._lin((gq, gs), f"w2{l}", **down)
             elif f16_ffn:  # fp16 operands (x1, W1, gelu(f1), W2); f1 is kept in bf16 for the backward, which re-creates gelu(f1) in bf16
-                gah = ops.gemm_nt(x1h, st[f"w1h{l}"], bias=v(p + "intermediate.dense.bias"), act=1, preact=f1)
-                z2 = ops.gemm_nt(gah, st[f"w2h{l}"], bias=v(p + "output.dense.bias"), drop=d_h2, residual=res1, out_f32=True, residual_ln=res1_ln)
+                gah = ops.gemm_nt(x1h, st[f"w1h{l}"], bias=P.w1_b, act=1, preact=f1)
+                z2 = ops.gemm_nt(gah, st[f"w2h{l}"], **down)
                 ga = None
             else:
                 # (fp8: the FFN-up epilogue writes gelu(f1) as the FFN-down's e4m3 operand itself; the bf16 copy only when the
                 # backward will want it -- the no-grad pass of gradient caching skips it)
-                ga, ga8 = self._lin(x1, f"w1{l}", emit8=f"w2{l}", keep16=save, bias=v(p + "intermediate.dense.bias"), act=1, preact=f1)
-                z2 = self._lin(ga8 if ga8 is not None else ga, f"w2{l}", bias=v(p + "output.dense.bias"), drop=d_h2, residual=res1, out_f32=r32,
-                               residual_ln=res1_ln)
+                ga, ga8 = self._lin_emit(x1, f"w1{l}", f"w2{l}", keep16=save, bias=P.w1_b, act=1, preact=f1)
+                z2 = self._lin(ga8 if ga8 is not None else ga, f"w2{l}", **down)
             if r32:
-                g2, b2 = v(p + "output.LayerNorm.weight"), v(p + "output.LayerNorm.bias")
-                last16 = self.fwd_f16 and l == cfg.num_hidden_layers - 1  # the head transform's fp16 operand
-                ln2 = ops.layernorm_fwd_res32(z2, g2, b2, eps, x.dtype, want_y32=False, want_y16=last16)
+                last16 = self.fwd_f16 and l == last  # the head transform's fp16 operand
+                ln2 = ops.layernorm_fwd_res32(z2, *P.ln2, eps, x.dtype, want_y32=False, want_y16=last16)
                 x2, _, m2, r2 = ln2[:4]
                 if last16:
                     xh_last = ln2[4]
-                x32, res_ln = z2, (m2, r2, g2, b2)
+                x32, res_ln = z2, (m2, r2, *P.ln2)
             else:
-                x2, m2, r2 = ops.layernorm_fwd(z2, v(p + "output.LayerNorm.weight"), v(p + "output.LayerNorm.bias"), eps)
+                x2, m2, r2 = ops.layernorm_fwd(z2, *P.ln2, eps)
             if save:
-                saved["layers"].append((x, qkv, ctx, lse, z1, m1, r1, x1, f1, ga, z2, m2, r2))
+                saved.append(_LayerSaved(x, qkv, ctx, lse, z1, m1, r1, x1, f1, ga, z2, m2, r2, _FFN.F16 if f16_ffn else _FFN.PLAIN,
+                                         d_at, d_h1, d_h2))
             x = x2
         self._x_last_f16 = xh_last
-        return x, saved
+        return x, emb_saved, saved
 
     def probe_density(self, rep: Tensor) -> None:
         """Start counting the live entries of `rep` (every 16th column) and take over the count of the PREVIOUS call: the host never
@@ -746,7 +794,7 @@ class HipBertMLM(torch.nn.Module):
         S0 = input_ids.shape[1]
         ids, mask, B, S = self._prep_inputs(input_ids, attention_mask)
         with torch.no_grad():
-            x, _ = self._forward_impl(ids, mask, B, S, False, 0, False)
+            x = self._forward_impl(ids, mask, B, S, False, 0, False)[0]
         return x.view(B, S, -1)[:, :S0].float()
 
     def encode(self, input_ids: Tensor, attention_mask: Tensor, use_l0: bool = False,
@@ -994,18 +1042,15 @@ class _EncodeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, model: HipBertMLM, ids, mask, B, S, use_l0, prune_ratio, training, seed, need_grad, rag, hints=None):
         cfg = model.config
-        x, saved = model._forward_impl(ids, mask, B, S, training, seed, need_grad, rag)
-        v, st = model.view, model._staged
-        c = "cls.predictions."
+        x, emb_saved, saved = model._forward_impl(ids, mask, B, S, training, seed, need_grad, rag)
+        st, Hd = model._staged, model._handles()[2]
         ft = torch.empty_like(x) if need_grad else None
         if model.fwd_f16:
             # fp16 operands for the transform GEMM (when the last layer left an fp16 copy of its output) and for the decoder GEMM
             # of the fused head; gelu(transform) stays fp32 between the GEMM epilogue and its LayerNorm
             xh = model._x_last_f16
-            gt = ops.gemm_nt(xh if xh is not None else x, st["t16"] if xh is not None else st["t"], bias=v(c + "transform.dense.bias"),
-                             act=1, preact=ft, out_f32=True)
-            tn, _, mt, rt, tn16 = ops.layernorm_fwd_res32(gt, v(c + "transform.LayerNorm.weight"), v(c + "transform.LayerNorm.bias"),
-                                                          cfg.layer_norm_eps, x.dtype, want_y32=False, want_y16=True)
+            gt = ops.gemm_nt(xh if xh is not None else x, st["t16"] if xh is not None else st["t"], bias=Hd.t_b, act=1, preact=ft, out_f32=True)
+            tn, _, mt, rt, tn16 = ops.layernorm_fwd_res32(gt, *Hd.ln, cfg.layer_norm_eps, x.dtype, want_y32=False, want_y16=True)
             if model.check_finite:
                 # fp16 has 5 exponent bits: an activation beyond 65 504 becomes inf in the fp16 operand copies (the bf16 path has fp32's
                 # range).  check_finite mode looks at the two fp16 tensors this layer of the code can see and names the remedy.
@@ -1013,13 +1058,12 @@ class _EncodeFn(torch.autograd.Function):
                     if t16 is not None and not bool(torch.isfinite(t16).all()):
                         raise FloatingPointError(f"fp16 forward operand overflow in the {name}: activations exceed the fp16 range "
                                                  "(65504); run this model with fwd_f16=False (ModelArguments.fwd_f16 / SM_FWD_F16=0)")
-            rep, argmax = ops.sparse_head_fwd(tn16, st["E16"], v(c + "bias"), mask, B, S, cfg.vocab_size, use_l0, rag)
+            rep, argmax = ops.sparse_head_fwd(tn16, st["E16"], Hd.bias, mask, B, S, cfg.vocab_size, use_l0, rag)
             del tn16
         else:
-            gt = ops.gemm_nt(x, st["t"], bias=v(c + "transform.dense.bias"), act=1, preact=ft)
-            tn, mt, rt = ops.layernorm_fwd(gt, v(c + "transform.LayerNorm.weight"), v(c + "transform.LayerNorm.bias"),
-                                           cfg.layer_norm_eps)
-            rep, argmax = ops.sparse_head_fwd(tn, st["E"], v(c + "bias"), mask, B, S, cfg.vocab_size, use_l0, rag)
+            gt = ops.gemm_nt(x, st["t"], bias=Hd.t_b, act=1, preact=ft)
+            tn, mt, rt = ops.layernorm_fwd(gt, *Hd.ln, cfg.layer_norm_eps)
+            rep, argmax = ops.sparse_head_fwd(tn, st["E"], Hd.bias, mask, B, S, cfg.vocab_size, use_l0, rag)
         if prune_ratio is not None:
             ops.prune_rows(rep, prune_ratio)
         if need_grad and model.dt_scatter:
@@ -1027,9 +1071,9 @@ class _EncodeFn(torch.autograd.Function):
         if model._argmax_log is not None:  # test hook: which position each (doc, vocab) max came from
             model._argmax_log.append(argmax)
         if need_grad:
-            ctx.model, ctx.saved = model, saved
-            ctx.head = (x, ft, gt, mt, rt, tn, rep, argmax)
-            ctx.meta = (ids, mask, B, S, use_l0, training, seed, rag)
+            ctx.model, ctx.emb, ctx.saved = model, emb_saved, saved
+            ctx.head = _HeadSaved(x, ft, gt, mt, rt, tn, rep, argmax)
+            ctx.meta = _Meta(ids, mask, B, S, use_l0, rag)
             ctx.hints = hints
         return rep
 
@@ -1037,123 +1081,97 @@ class _EncodeFn(torch.autograd.Function):
     def backward(ctx, grad_rep):
         model: HipBertMLM = ctx.model
         cfg = model.config
-        ids, mask, B, S, use_l0, training, seed, rag = ctx.meta
-        x_last, ft, gt, mt, rt, tn, rep, argmax = ctx.head
-        A = cfg.num_attention_heads
-        ph, pa = cfg.hidden_dropout_prob, cfg.attention_probs_dropout_prob
+        M, hd, emb, saved = ctx.meta, ctx.head, ctx.emb, ctx.saved
+        nl, A = cfg.num_hidden_layers, cfg.num_attention_heads
         st = model._staged
-        v = model.view
-        g = lambda n: model.view(n, grad=True)
-        c = "cls.predictions."
-        e = "bert.embeddings."
+        E, layers, Hd = model._handles()
+        dims = (M.B, M.S, cfg.vocab_size, M.use_l0, M.rag)
         if model._wgrad is None:
             model._wgrad = _WgradStream(model.device, model.wgrad_stream, model.tn_group)
         wg = model._wgrad
         grad_rep = grad_rep.contiguous().float()
         # the head backward's two halves: dE / dbias are weight gradients (side stream, like every other one),
         # dt continues the chain
-        head_args = (grad_rep, rep, argmax, tn, st["E"], g(e + "word_embeddings.weight"), g(c + "bias"), B, S, cfg.vocab_size, use_l0, rag)
-        wg.call(lambda: ops.sparse_head_bwd(*head_args, part="de"), grad_rep, rep, argmax, tn)
+        head_args = (grad_rep, hd.rep, hd.argmax, hd.tn, st["E"], E.grad.word, Hd.grad.bias, *dims)
+        wg.call(lambda: ops.sparse_head_bwd(*head_args, part="de"), grad_rep, hd.rep, hd.argmax, hd.tn)
         head_de_done = wg.mark()
         scatter = (model.dt_scatter and model._density is not None and model._density < model.dt_scatter_density
                    and st["E"].dtype == torch.bfloat16)
-        dft = None if scatter else ops.sparse_head_bwd_dt_ln(grad_rep, rep, argmax, st["E"], B, S, cfg.vocab_size, use_l0, rag, gt,
-                                                             v(c + "transform.LayerNorm.weight"), mt, rt, ft,
-                                                             g(c + "transform.LayerNorm.weight"), g(c + "transform.LayerNorm.bias"))
+        dft = None if scatter else ops.sparse_head_bwd_dt_ln(grad_rep, hd.rep, hd.argmax, st["E"], *dims, hd.gt, Hd.ln[0], hd.mt, hd.rt,
+                                                             hd.ft, *Hd.grad.ln)
         if dft is None:
-            dtn = (ops.sparse_head_bwd_dt_scatter(grad_rep, rep, argmax, st["E"], B, S, cfg.vocab_size, use_l0, rag, tn.shape[0])
+            dtn = (ops.sparse_head_bwd_dt_scatter(grad_rep, hd.rep, hd.argmax, st["E"], *dims, hd.tn.shape[0])
                    if scatter else ops.sparse_head_bwd(*head_args, part="dt"))
-            dgt, _ = ops.layernorm_bwd(dtn, gt, v(c + "transform.LayerNorm.weight"), mt, rt,
-                                       g(c + "transform.LayerNorm.weight"), g(c + "transform.LayerNorm.bias"))
-            dft = ops.gelu_bwd(dgt, ft)
-        wg.run(dft, x_last, g(c + "transform.dense.weight"), g(c + "transform.dense.bias"))
-        # the transform's input gradient feeds the output LayerNorm of the last layer: GEMM + LayerNorm backward in one launch
-        # where the kernel takes the shape (pending = (dz2, dz2d) of the layer about to run)
-        pending = None
-        if cfg.num_hidden_layers > 0:
-            pl = f"bert.encoder.layer.{cfg.num_hidden_layers - 1}."
-            z2l, m2l, r2l = ctx.saved["layers"][-1][10:13]
-            d_h2l = model._drop(ph, training, seed, cfg.num_hidden_layers, _Site.HID2)
-            pending = ops.gemm_nt_ln_bwd(dft, st["tT"], None, z2l, v(pl + "output.LayerNorm.weight"), m2l, r2l,
-                                         g(pl + "output.LayerNorm.weight"), g(pl + "output.LayerNorm.bias"),
-                                         d_h2l, want_drop=d_h2l is not None)
+            dgt, _ = ops.layernorm_bwd(dtn, hd.gt, Hd.ln[0], hd.mt, hd.rt, *Hd.grad.ln)
+            dft = ops.gelu_bwd(dgt, hd.ft)
+        wg.run(dft, hd.x, Hd.grad.t_w, Hd.grad.t_b)
+
+        def into_ln2(l, dy, wt, residual):
+            """dy . W^T (+ residual) and the backward of layer l's output LayerNorm, which consumes it, in one launch where the
+            kernel takes the shape: (dz2, dz2d) of layer l, otherwise None"""
+            r, P = saved[l], layers[l]
+            return ops.gemm_nt_ln_bwd(dy, st[wt], residual, r.z2, P.ln2[0], r.m2, r.r2, *P.grad.ln2, r.d_h2, want_drop=r.d_h2 is not None)
+
+        # the transform's input gradient feeds the output LayerNorm of the last layer (pending = (dz2, dz2d) of the layer about to run)
+        pending = into_ln2(nl - 1, dft, "tT", None) if nl > 0 else None
         if pending is None:
             dx = ops.gemm_nt(dft, st["tT"])
         if model._layer_hook is not None:
             model._layer_hook("head", wg.mark())
         deferred_layer = None
-        for l in reversed(range(cfg.num_hidden_layers)):
-            p = f"bert.encoder.layer.{l}."
-            x, qkv, ctxt, lse, z1, m1, r1, x1, f1, ga, z2, m2, r2 = ctx.saved["layers"][l]
-            d_at = model._drop(pa, training, seed, l + 1, _Site.ATTN)
-            d_h1 = model._drop(ph, training, seed, l + 1, _Site.HID1)
-            d_h2 = model._drop(ph, training, seed, l + 1, _Site.HID2)
+        for l in reversed(range(nl)):
+            r, P, G = saved[l], layers[l], layers[l].grad
             if pending is not None:
                 dz2, dz2d = pending
                 pending = None
             else:
-                dz2, dz2d = ops.layernorm_bwd(dx, z2, v(p + "output.LayerNorm.weight"), m2, r2,
-                                              g(p + "output.LayerNorm.weight"), g(p + "output.LayerNorm.bias"),
-                                              d_h2, want_drop=d_h2 is not None)
-            a2 = dz2d if d_h2 is not None else dz2
-            fused = None
-            if ga is None and model.pc_ffn_bwd and f1.dim() == 4:  # the fused feed-forward's backward: dF1, gelu(f1), dz1 from one launch
-                fb = ops.ffn_pc_bwd(a2, dz2, f1, st["pc_w2tf"][l], st["pc_w1tf"][l], z1, v(p + "attention.output.LayerNorm.weight"), m1, r1,
-                                    d_h1, g(p + "attention.output.LayerNorm.weight"), g(p + "attention.output.LayerNorm.bias"),
-                                    want_drop=d_h1 is not None)
+                dz2, dz2d = ops.layernorm_bwd(dx, r.z2, P.ln2[0], r.m2, r.r2, *G.ln2, r.d_h2, want_drop=r.d_h2 is not None)
+            a2 = dz2d if r.d_h2 is not None else dz2
+            # backward of the attention-output LayerNorm (and of the dropout before it), as layernorm_bwd and gemm_nt_ln_bwd take it
+            ln1, drop1 = (r.z1, P.ln1[0], r.m1, r.r1, *G.ln1, r.d_h1), r.d_h1 is not None
+            ga, fused, df18 = r.ga, None, None
+            if r.form == _FFN.FUSED and model.pc_ffn_bwd:  # the fused feed-forward's backward: dF1, gelu(f1), dz1 from one launch
+                fb = ops.ffn_pc_bwd(a2, dz2, r.f1, st["pc_w2tf"][l], st["pc_w1tf"][l], r.z1, P.ln1[0], r.m1, r.r1, r.d_h1, *G.ln1, want_drop=drop1)
                 if fb is not None:
                     df1, ga, dz1, dz1d = fb
                     fused = (dz1, dz1d)
-                    wg.run(a2, ga, g(p + "output.dense.weight"), g(p + "output.dense.bias"))
-            df18 = None
-            if fused is not None:
-                pass
-            elif ga is not None:
-                wg.run(a2, ga, g(p + "output.dense.weight"), g(p + "output.dense.bias"))
-                gsite = model._fp8_gelu_site(f"w1T{l}", a2.device) if f1.dim() == 2 else None
+                    wg.run(a2, ga, G.w2_w, G.w2_b)
+            if fused is None and r.form == _FFN.PLAIN:
+                wg.run(a2, ga, G.w2_w, G.w2_b)
+                gsite = model._fp8_gelu_site(f"w1T{l}", a2.device)
                 if gsite is not None:  # fp8: the plain product, then x gelu'(f1) and the e5m2 copy in one pass (the epilogue form: 1 213 against 469 us)
                     raw = model._lin(a2, f"w2T{l}", grad=True)
-                    df1, dq, dsc = ops.gelu_quantize_fp8(raw, gsite[0], gsite[1], f1=f1, inplace=True)
+                    df1, dq, dsc = ops.gelu_quantize_fp8(raw, gsite[0], gsite[1], f1=r.f1, inplace=True)
                     df18 = (dq, dsc)
                 else:
                     # (fp8: dF1 leaves this epilogue in bf16 for the weight gradient AND as the e5m2 operand of the FFN-up input gradient)
-                    df1, df18 = model._lin(a2, f"w2T{l}", grad=True, emit8=f"w1T{l}", emit8_grad=True, gelu_grad_of=f1)
-            else:  # the forward ran on fp16 operands and kept gelu(f1) in fp16 only: the dF1 epilogue re-creates it in bf16
-                ga = torch.empty((a2.shape[0], cfg.intermediate_size), dtype=f1.dtype, device=f1.device)
-                df1 = ops.gemm_nt(a2, st[f"w2T{l}"], gelu_grad_of=f1, gelu_out=ga, gelu_grad_tiled=f1.dim() == 4)
-                wg.run(a2, ga, g(p + "output.dense.weight"), g(p + "output.dense.bias"))
-            wg.run(df1, x1, g(p + "intermediate.dense.weight"), g(p + "intermediate.dense.bias"))
+                    df1, df18 = model._lin_emit(a2, f"w2T{l}", f"w1T{l}", grad=True, gelu_grad_of=r.f1)
+            elif fused is None:  # gelu(f1) was not kept (fp16 operands had it in fp16 only; the fused kernel never wrote it): the dF1 epilogue re-creates it in bf16
+                ga = torch.empty((a2.shape[0], cfg.intermediate_size), dtype=r.f1.dtype, device=r.f1.device)
+                df1 = ops.gemm_nt(a2, st[f"w2T{l}"], gelu_grad_of=r.f1, gelu_out=ga, gelu_grad_tiled=r.form == _FFN.FUSED)
+                wg.run(a2, ga, G.w2_w, G.w2_b)
+            wg.run(df1, r.x1, G.w1_w, G.w1_b)
             # FFN-up input gradient + residual, fused with the LayerNorm backward that consumes it where the kernel
             # takes the shape (hidden 384, long K): the [T, H] gradient in between never goes to HBM
-            if fused is None:
-                fused = None if model.fp8 else ops.gemm_nt_ln_bwd(df1, st[f"w1T{l}"], dz2, z1, v(p + "attention.output.LayerNorm.weight"), m1, r1,
-                                       g(p + "attention.output.LayerNorm.weight"), g(p + "attention.output.LayerNorm.bias"),
-                                       d_h1, want_drop=d_h1 is not None)
+            if fused is None and not model.fp8:
+                fused = ops.gemm_nt_ln_bwd(df1, st[f"w1T{l}"], dz2, *ln1, want_drop=drop1)
             if fused is not None:
                 dz1, dz1d = fused
             else:
                 dx1 = model._lin(df18 if df18 is not None else df1, f"w1T{l}", grad=True, residual=dz2)
-                dz1, dz1d = ops.layernorm_bwd(dx1, z1, v(p + "attention.output.LayerNorm.weight"), m1, r1,
-                                              g(p + "attention.output.LayerNorm.weight"),
-                                              g(p + "attention.output.LayerNorm.bias"), d_h1, want_drop=d_h1 is not None)
-            a1 = dz1d if d_h1 is not None else dz1
-            wg.run(a1, ctxt, g(p + "attention.output.dense.weight"), g(p + "attention.output.dense.bias"))
+                dz1, dz1d = ops.layernorm_bwd(dx1, *ln1, want_drop=drop1)
+            a1 = dz1d if drop1 else dz1
+            wg.run(a1, r.ctx, G.o_w, G.o_b)
             dctx = model._lin(a1, f"oT{l}", grad=True)
-            dqkv = ops.attention_bwd(qkv, mask, ctxt, dctx, lse, B, S, A, d_at, rag)
-            wg.run(dqkv, x, model.qkv_weight(l, grad=True), model.qkv_bias(l, grad=True))
-            if l > 0:  # the QKV input gradient feeds the output LayerNorm of layer l-1: same fusion
-                pp = f"bert.encoder.layer.{l - 1}."
-                z2p, m2p, r2p = ctx.saved["layers"][l - 1][10:13]
-                d_h2p = model._drop(ph, training, seed, l, _Site.HID2)
-                pending = None if model.fp8 else ops.gemm_nt_ln_bwd(dqkv, st[f"qkvT{l}"], dz1, z2p, v(pp + "output.LayerNorm.weight"), m2p, r2p,
-                                             g(pp + "output.LayerNorm.weight"), g(pp + "output.LayerNorm.bias"),
-                                             d_h2p, want_drop=d_h2p is not None)
+            dqkv = ops.attention_bwd(r.qkv, M.mask, r.ctx, dctx, r.lse, M.B, M.S, A, r.d_at, M.rag)
+            wg.run(dqkv, r.x, G.qkv_w, G.qkv_b)
             dz0 = None
-            if l == 0:  # ... and of the embedding LayerNorm (with the embedding dropout in between)
-                z0, m0, r0 = ctx.saved["emb"]
-                d_emb = model._drop(ph, training, seed, 0, _Site.EMB)
-                fused = None if model.fp8 else ops.gemm_nt_ln_bwd(dqkv, st[f"qkvT{l}"], dz1, z0, v(e + "LayerNorm.weight"), m0, r0,
-                                           g(e + "LayerNorm.weight"), g(e + "LayerNorm.bias"), dy_drop=d_emb)
+            if model.fp8:
+                pass
+            elif l > 0:  # the QKV input gradient feeds the output LayerNorm of layer l-1: same fusion
+                pending = into_ln2(l - 1, dqkv, f"qkvT{l}", dz1)
+            else:  # ... and of the embedding LayerNorm (with the embedding dropout in between)
+                fused = ops.gemm_nt_ln_bwd(dqkv, st[f"qkvT{l}"], dz1, emb.z0, E.ln[0], emb.m0, emb.r0, *E.grad.ln, dy_drop=emb.d_emb)
                 if fused is not None:
                     dz0 = fused[0]
             if pending is None and dz0 is None:
@@ -1164,7 +1182,6 @@ class _EncodeFn(torch.autograd.Function):
             # backward chain stays one layer long).  With a gradient-reduction hook (N > 1) the pair's two slices of the flat
             # gradient -- adjacent in the buffer -- are reduced by ONE collective behind the pair's launch (round 6; rounds 2-5
             # flushed and reduced per layer whenever a hook was set).
-            nl = cfg.num_hidden_layers
             if not model.tn_pair or l == nl - 1 or l == 0 or (nl - 1 - l) % 2 == 0:
                 wg.flush()
                 if model._layer_hook is not None:
@@ -1172,32 +1189,14 @@ class _EncodeFn(torch.autograd.Function):
                 deferred_layer = None
             else:
                 deferred_layer = l  # its products wait for the next layer's flush
-        z0, m0, r0 = ctx.saved["emb"]
-        if cfg.num_hidden_layers == 0 or dz0 is None:
-            d_emb = model._drop(ph, training, seed, 0, _Site.EMB)
-            if d_emb is not None:
-                dx = ops.dropout_bwd(dx, d_emb)
-            dz0, _ = ops.layernorm_bwd(dx, z0, v(e + "LayerNorm.weight"), m0, r0, g(e + "LayerNorm.weight"),
-                                       g(e + "LayerNorm.bias"))
+        if nl == 0 or dz0 is None:
+            if emb.d_emb is not None:
+                dx = ops.dropout_bwd(dx, emb.d_emb)
+            dz0, _ = ops.layernorm_bwd(dx, emb.z0, E.ln[0], emb.m0, emb.r0, *E.grad.ln)
         if head_de_done is not None:  # both add into the tied word-embedding gradient, the head's half without atomics
             torch.cuda.current_stream().wait_event(head_de_done)
-        hints = getattr(ctx, "hints", None)
-        ops.embed_bwd(dz0, ids, g(e + "word_embeddings.weight"), g(e + "position_embeddings.weight"),
-                      g(e + "token_type_embeddings.weight")[0], rag, srt=hints.emb_sorted if hints is not None else None)
+        ops.embed_bwd(dz0, M.ids, E.grad.word, E.grad.pos, E.grad.type[0], M.rag, srt=ctx.hints.emb_sorted if ctx.hints is not None else None)
         wg.join()
-        ctx.saved = ctx.head = None
+        ctx.saved = ctx.head = ctx.emb = None
         model._reattach_grads()
         return (None,) * 13
-
-
-HipBertMLM._layer_hook = None
-HipBertMLM.check_finite = False  # TrainingArguments.check_finite / SM_CHECK_FINITE: also look for fp16 operand overflow in the forward
-HipBertMLM._dropout_without_grad = False
-HipBertMLM._cast_table = None
-HipBertMLM._cast_key = None
-HipBertMLM._cast_table16 = None
-HipBertMLM._small_ffn16 = False
-HipBertMLM._cast_key16 = None
-HipBertMLM._x_last_f16 = None
-HipBertMLM._wgrad = None
-HipBertMLM._argmax_log = None

@@ -288,3 +288,44 @@ def test_dense_embed_hints_sort_the_attended_rows():
     assert rows_id.tolist() == [1, 16, 0, 2, 32, 17]          # b * 16 + s, stable inside a run
     assert pos_sorted.tolist() == [0, 0, 0, 1, 1, 2] and rows_pos.tolist() == [0, 16, 32, 1, 17, 2]
     assert dense_embed_hints(ids, mask, "cpu", 2) is None     # the device layout cannot be narrower than the batch
+
+
+def test_parameter_handles_reach_every_layout_name_once_and_alias_the_flat_buffers():
+    """HipBertMLM._handles(): the per-layer, embedding and head handles the forward, the backward and sync_weights() read their
+    parameters through.  Every name of param_layout() is reachable through exactly one attribute (a LayerNorm's (gamma, beta) pair
+    and the fused q/k/v spans count for each of their names), parameter and gradient side are the very views view() hands out, and
+    they still are after zero_grad() (which must clear the buffer in place)"""
+    from sparse_hip.encoder import BertConfigLite, HipBertMLM, param_layout
+    cfg = BertConfigLite(vocab_size=100, hidden_size=128, num_hidden_layers=2, num_attention_heads=4, intermediate_size=256)
+    bb = HipBertMLM(cfg, device="cpu", init_seed=None)
+    emb, layers, head = bb._handles()
+    assert len(layers) == cfg.num_hidden_layers
+
+    def reachable():
+        seen, tensors = [], []
+        for h in (emb, *layers, head):
+            for attr, names in h.names.items():
+                for grad, side in ((False, h), (True, h.grad)):
+                    val = getattr(side, attr)
+                    # a tuple is a LayerNorm's (gamma, beta); one tensor under several names is the span of adjacent equal tensors
+                    parts = val if isinstance(val, tuple) else val.chunk(len(names))
+                    assert len(parts) == len(names), attr
+                    for name, t in zip(names, parts):
+                        ref = bb.view(name, grad=grad)
+                        assert t.data_ptr() == ref.data_ptr() and t.shape == ref.shape, (name, grad)
+                        if grad:
+                            tensors.append(t)
+                seen += names
+        return seen, tensors
+
+    seen, _ = reachable()
+    assert len(seen) == len(set(seen)) and sorted(seen) == sorted(n for n, _ in param_layout(cfg))
+    assert layers[0].qkv_w.shape == (384, 128) and layers[1].grad.qkv_b.shape == (384,)
+    bb.flat_grad.fill_(1.0)
+    assert float(layers[1].grad.ln2[1].sum()) == 128.0  # a write to the flat buffer shows through the handle
+    bb.zero_grad()
+    _, grads = reachable()
+    assert all(not bool(t.any()) for t in grads)
+    with torch.no_grad():
+        bb.flat_param.add_(1.0)  # an in-place optimiser update
+    assert bool((head.bias == 1.0).all()) and bool((emb.ln[0] == 1.0).all())

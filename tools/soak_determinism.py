@@ -10,12 +10,15 @@ the list with the first iteration's.  A mismatch that shows up rarely is a race 
 `torch.empty` is replaced by `torch.zeros` for the run so that rows a kernel legitimately leaves unwritten compare equal.
 
   python tools/soak_determinism.py --iters 200 [--layout ragged|dense] [--dropout 0.1] [--queries 8 --docs 4] [--perturb]
-                                   [--sync-each-op]
+                                   [--sync-each-op] [--dump FILE]
+--dump FILE: iteration 0 only, written as a JSON list of the step's ops calls in call order (see --help): the same launches in
+the same order on the same streams with bit-equal tensors give byte-identical files, whatever the host code that enqueued them.
 --perturb: a second thread keeps a matrix product running on its own stream (the step's kernels then see changing numbers of
 free CUs and different memory latencies).  Exit code 1 when a non-atomic tensor ever differed.
 """
 import argparse
 import inspect
+import json
 import os
 import socket
 import subprocess
@@ -30,7 +33,7 @@ for p in (ROOT, os.path.join(ROOT, "opensearch-sparse-model-tuning-sample_amd"),
 
 import torch  # noqa: E402
 
-REC = {"on": False, "items": [], "skip": (0, 0), "sync": False}
+REC = {"on": False, "items": [], "calls": [], "skip": (0, 0), "sync": False}
 
 
 def _tensors(obj, prefix=""):
@@ -73,10 +76,12 @@ def install():
         def g(*a, **k):
             r = f(*a, **k)
             if REC["on"]:
+                call = len(REC["calls"])
+                REC["calls"].append((name, torch.cuda.current_stream() == torch.cuda.default_stream()))
                 for slot, t in list(_tensors(r, "ret")) + list(_tensors([a, k], "arg")):
                     c = _checksum(t)
                     if c is not None:
-                        REC["items"].append((name, slot, tuple(t.shape), c))
+                        REC["items"].append((name, slot, tuple(t.shape), c, call))
                 if REC["sync"]:
                     torch.cuda.synchronize()
             return r
@@ -129,6 +134,9 @@ def main():
     ap.add_argument("--fp8", action="store_true")
     ap.add_argument("--perturb", action="store_true")
     ap.add_argument("--sync-each-op", action="store_true")
+    ap.add_argument("--dump", metavar="FILE", help="run iteration 0 only and write its ops calls, in call order, as JSON: [entry point, ran on the "
+                    "default stream, sorted [shape, checksum] of its tensors]; two dumps of the same launches compare equal with cmp.  "
+                    "With --fp8 the weights are marked dirty before each iteration, so iteration 0 runs on delayed scales")
     args = ap.parse_args()
     print("box:", box_identity(), flush=True)
     import collapse_hunt as H
@@ -150,21 +158,34 @@ def main():
     for it in range(-1, args.iters):  # iteration -1: warm-up (staging copies are made there), not compared
         trainer.zero_grad()
         bb.set_dropout_seed(777)
-        REC["items"], REC["on"] = [], True
+        if args.dump and args.fp8:
+            bb.mark_weights_dirty()
+        REC["items"], REC["calls"], REC["on"] = [], [], True
         loss = trainer.compute_loss(trainer.model, inp)
         loss.backward()
         REC["on"] = False
         torch.cuda.synchronize()
         if it < 0:
             continue
-        meta = [(n, s, sh) for n, s, sh, _ in REC["items"]]
-        sums = torch.stack([c for _, _, _, c in REC["items"]]).cpu()
+        meta = [(n, s, sh) for n, s, sh, _, _ in REC["items"]]
+        sums = torch.stack([item[3] for item in REC["items"]]).cpu()
         finite = bool(torch.isfinite(bb.flat_grad).all())
         losses.add(float(loss.detach()))
         if ref is None:
             ref, ref_meta = sums, meta
             print(f"iteration 0: {len(meta)} checksummed tensors over {len(set(n for n, _, _ in meta))} entry points, loss {float(loss):.6f}, "
                   f"gradients finite: {finite}", flush=True)
+            if args.dump:
+                out = [[n, dflt, []] for n, dflt in REC["calls"]]
+                for (_, _, sh, _, call), c in zip(REC["items"], sums.tolist()):
+                    out[call][2].append([list(sh), c])
+                for entry in out:
+                    entry[2].sort()
+                with open(args.dump, "w") as f:
+                    json.dump(out, f, separators=(",", ":"))
+                print(f"dump: {len(out)} calls, {len(meta)} tensors -> {args.dump}")
+                stop.set()
+                return 0
             continue
         if meta != ref_meta:
             print(f"iteration {it}: the sequence of launches changed ({len(meta)} against {len(ref_meta)})")
