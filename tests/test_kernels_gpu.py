@@ -956,8 +956,10 @@ def test_sparse_head_ragged_layout(ops, dtype, H, use_l0):
 @pytest.mark.parametrize("A,dh,S,doc_lens", [(2, 32, 128, [37, 128, 16, 90, 5, 64]), (3, 64, 512, [300, 512, 17, 129, 480, 64, 255]),
                                              (2, 64, 256, [256, 100, 31]), (3, 32, 512, [511, 48, 200])])
 def test_attention_ragged_layout(ops, dtype, A, dh, S, doc_lens):
-    """un-padded documents against the per-document eager attention; the long-document shapes (configs[4]: head dim 64, up to 512
-    tokens) run 8 waves per workgroup forward and 12 backward over one document's K / V images"""
+    """un-padded documents against the per-document eager attention.  What launch_fwd / launch_bwd pick for these rows in bf16 (the
+    table of tests/test_attention_gpu.py): (2, 32, 128) 4 waves forward and attn_bwd1_kernel; (2, 64, 256) 8 waves forward, the two-phase
+    backward with 12; (3, 64, 512) (configs[4]: head dim 64, up to 512 tokens) and (3, 32, 512) (unpaired heads) the two-group forward with
+    16 waves and the two-phase backward with 12.  fp32 parity mode: 4 waves everywhere"""
     if dtype == torch.float32 and S * dh > 256 * 64:
         pytest.skip("fp32 parity mode: two [S][dh] fp32 LDS images cap S*dh at 256*64")
     lens, off, rows, row_doc, pos, valid = _ragged(doc_lens)
